@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- IRR-PWC train-step throughput on MI355X (BASELINE.json metric: image-pairs/sec fwd+bwd).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up and exactly K timed steps of the headline workload and prints its line: ``metric`` / ``value``
+(image-pairs/s over the K steps) / ``ms_per_step`` and the run's configuration; nothing else runs on the GPU or the host.
+``--full`` adds everything that needs work of its own: per-launch HIP events on the timed steps (``roofline``), one extra step for
+``launches_per_step``, the 448x1024 ``secondary`` leg and the further legs and CPU baselines described below.
+``--dump-outputs DIR`` writes what the last timed step returned to its caller (losses, every flow / occlusion output) as
+``DIR/<name>.npy`` (float32; arrays larger than their share of a 48 MiB budget as a fixed, seeded sample of their elements), so that
+two builds can be compared output for output on identical inputs.  Every step starts from the weights and Adam moments its leg
+started with (restored before each step: three device copies of 25 MB), so that what a step computes depends only on its batch:
+the weight gradients are accumulated with fp32 atomics, and Adam would turn their rounding-level differences into run-to-run
+differences of percents in the outputs of later steps.
 
 N > 1: one rank per GPU over RCCL.  Either started by ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...``
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or from a plain shell: the script then starts those N ranks itself as
@@ -11,11 +22,11 @@ A "step" is one pass of the hot path over one synthetic batch: zero_grad -> PWCN
 MultiScaleEPE_PWC_Bi_Occ_upsample -> NaN check -> backward -> [RCCL gradient all-reduce] -> Adam step,
 i.e. the reference's TrainingEpoch._step (runtime.py:131-194) with inputs already resident in HBM.
 Workload = BASELINE configs[2] (384x448, 32 pairs per GPU, FlyingChairsOcc-shaped synthetic tensors,
-weak scaling: every rank gets its own 32 pairs).  Prints ONE JSON line on rank 0.  After the headline timing the same process
-runs 5 steps of the per-GPU workload of BASELINE configs[4] (448x1024, 8 pairs per GPU: north_star's second crop) and reports it
-under ``"secondary"`` (own roofline object); ``metric`` / ``value`` are the headline's.
+weak scaling: every rank gets its own 32 pairs).  Prints ONE JSON line on rank 0.  With ``--full``, after the headline timing the
+same process runs 5 steps of the per-GPU workload of BASELINE configs[4] (448x1024, 8 pairs per GPU: north_star's second crop) and
+reports it under ``"secondary"`` (own roofline object); ``metric`` / ``value`` are the headline's.
 
-Further keys of the line (rank 0, N = 1): ``reference_harness`` -- the same model under the REFERENCE's own loop, literally
+Further keys of the ``--full`` line (rank 0, N = 1): ``reference_harness`` -- the same model under the REFERENCE's own loop, literally
 (runtime.py:158-189: ``optimizer.zero_grad()``, forward, ``.item()`` NaN assertion before ``backward()``, stock
 ``torch.optim.Adam.step()``; no GradArena / FusedAdam / TrainStep), as a user who swaps the model class into runtime.py gets it
 (the model installs arena + lane itself, irr_amd/harness.py) and with that switched off (``plain_autograd``); ``forward_only`` --
@@ -68,6 +79,40 @@ TRAFFIC_FILES = {(384, 448, 32): "hbm_traffic.json", (448, 1024, 8): "hbm_traffi
 
 
 NBATCHES = 4                           # distinct synthetic batches resident in HBM, fed round-robin (no step sees the batch of the step before)
+DUMP_BUDGET_BYTES = 48 << 20           # --dump-outputs: all arrays together (float32)
+DUMP_SEED = 20240601                   # --dump-outputs: the element sample of an array larger than its share of the budget
+
+
+def dump_outputs(out_dir, loss_dict, output_dict):
+    """--dump-outputs: the last timed step's losses and outputs (what TrainStep returns to its caller) -> out_dir/<name>.npy.
+    Every array gets an equal share of DUMP_BUDGET_BYTES; a larger one is stored as the sorted sample of its flattened elements
+    drawn without replacement by numpy's default_rng([DUMP_SEED, k]) (k = the array's place in the list), the same from run to run.
+    -> {name: number of elements of the full array}"""
+    import numpy as np
+    arrays = [("loss_" + k, v) for k, v in sorted(loss_dict.items())]
+
+    def walk(name, v):
+        if isinstance(v, torch.Tensor):
+            arrays.append((name, v))
+        elif isinstance(v, dict):
+            for k in sorted(v):
+                walk(f"{name}_{k}", v[k])
+        else:
+            for j, e in enumerate(v):
+                walk(f"{name}_{j}", e)
+    for k in sorted(output_dict):
+        walk(k, output_dict[k])
+    share = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = {}
+    for k, (name, t) in enumerate(arrays):
+        flat = t.detach().reshape(-1).float()
+        if flat.numel() > share:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, k]).choice(flat.numel(), share, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy().reshape(t.shape if flat.numel() == t.numel() else -1))
+        sizes[name] = t.numel()
+    return sizes
 
 
 def cpu_model():
@@ -211,6 +256,11 @@ def main():
     ap.add_argument("--harness", choices=["own", "reference"], default="own",
                     help="own: TrainStep + GradArena + FusedAdam (headline); reference: the reference's literal loop as the headline")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip reference_harness / forward_only / single_stream")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline (kernel timer), launches_per_step, the secondary leg, the extra legs and the CPU "
+                         "baselines (the --no-* switches above pick from these); off: the headline's timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses and outputs to DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -283,8 +333,15 @@ def main():
             # the reference's per-step NaN assertion is ON: asserted before the optimizer step (TrainStep docstring);
             # IRR_BENCH_NANCHECK=before_backward: the reference's exact placement (A/B), =off: diagnostic
             nc = os.environ.get("IRR_BENCH_NANCHECK", "before_step")
-            return TrainStep(mal, opt, grad_sync=arena.sync,
-                             check_nan=False if (nc == "off" or os.environ.get("IRR_BENCH_NO_NANCHECK")) else nc)
+            st = TrainStep(mal, opt, grad_sync=arena.sync,
+                           check_nan=False if (nc == "off" or os.environ.get("IRR_BENCH_NO_NANCHECK")) else nc)
+            # every step of a leg starts from the weights and Adam moments the leg started with (run() calls this before each
+            # step; three device copies, 75 MB): the weight gradients are accumulated with fp32 atomics, and Adam turns their
+            # rounding-level run-to-run differences into parameter differences of the order of lr within a step or two, so a
+            # step taken from the state that earlier steps left behind would not be reproducible from run to run
+            snap = opt.snapshot()
+            st.restore_state = lambda: opt.restore(snap)
+            return st
         return make
 
     def reference_step_factory(model):
@@ -310,8 +367,9 @@ def main():
             return step
         return make
 
-    def run(make_step, batch_pairs, height, width, steps, warmup, timed_kernels):
-        """W untimed + exactly K timed train steps of one workload -> dict(dt, value, loss, routing, roofline)"""
+    def run(make_step, batch_pairs, height, width, steps, warmup, timed_kernels, count_launches=True, dump_dir=None):
+        """W untimed + exactly K timed train steps of one workload -> dict(dt, value, loss, routing, roofline, dumped); routing =
+        launches of one more step after the timed ones (``count_launches``); ``dump_dir``: dump_outputs() of the last timed step"""
         step = make_step(batch_pairs)
         batches = [synthetic_batch(batch_pairs, height, width, 1234 + rank + int(os.environ.get("IRR_BENCH_SEED_OFFSET", "0")) + 1000 * i, device) for i in range(NBATCHES)]   # (offset: diagnosis switch -- another rank's batches in a single process)
         marks = [] if os.environ.get("IRR_BENCH_STEPTIMES") else None      # diagnostic: per-step GPU time (events, no extra syncs)
@@ -322,8 +380,11 @@ def main():
                 ev.record()
                 marks.append((time.perf_counter(), ev))
 
+        reset = getattr(step, "restore_state", None)         # own harness: see own_step_factory
         for i in range(warmup):
             mark()
+            if reset is not None:
+                reset()
             step(batches[i % NBATCHES])
         seg0 = torch.cuda.memory_stats(device).get("segment.all.allocated", 0) if marks is not None else 0
         timer = None
@@ -331,16 +392,27 @@ def main():
             timer = C.KernelTimer()
             C.TIMER = timer
         barrier()
+        last_out = None
         t0 = time.perf_counter()
         for i in range(steps):
             mark()
             if timer is not None:
                 timer.begin_step(i % max(1, a.timer_every) == 0)
-            ld, _, _ = step(batches[(warmup + i) % NBATCHES])
+            if reset is not None:
+                reset()
+            ld, od, _ = step(batches[(warmup + i) % NBATCHES])
+            if dump_dir is not None and i == steps - 1:
+                last_out = od
+            del od
         mark()
         barrier()
         dt = time.perf_counter() - t0
         C.TIMER = None
+        dumped = None
+        if dump_dir is not None and rank == 0:
+            # before anything else runs on the device: the outputs exactly as the last timed step returned them
+            dumped = dump_outputs(dump_dir, ld, last_out)
+        del last_out
         if marks is not None and rank == 0:
             print("per-step ms (gpu / cpu issue), first %d are warm-up: " % warmup +
                   " ".join("%.1f/%.1f" % (m0[1].elapsed_time(m1[1]), 1e3 * (m1[0] - m0[0])) for m0, m1 in zip(marks[:-1], marks[1:])),
@@ -350,10 +422,12 @@ def main():
                   % (st.get("segment.all.allocated", 0) - seg0, st.get("segment.all.allocated", 0), st.get("num_alloc_retries", 0),
                      torch.cuda.max_memory_allocated(device) / 1e9, torch.cuda.max_memory_reserved(device) / 1e9), file=sys.stderr)
         # what one step was ROUTED to (launch counters of irr_amd.conv), taken on one extra step outside the timed region
-        C.LAUNCHES.clear()
-        step(batches[0])
-        torch.cuda.synchronize()
-        routing = dict(C.LAUNCHES)
+        routing = None
+        if count_launches:
+            C.LAUNCHES.clear()
+            step(batches[0])
+            torch.cuda.synchronize()
+            routing = dict(C.LAUNCHES)
         spread = None
         if dist_on:
             allt = torch.zeros(world, device=device, dtype=torch.float64)      # every rank fills its slot: SUM == gather
@@ -362,7 +436,7 @@ def main():
             per_rank = [float(t) for t in allt.tolist()]
             dt = max(per_rank)                                                 # MAX over ranks
             spread = {"per_rank_ms_per_step": [round(t / steps * 1e3, 3) for t in per_rank]}
-        res = {"dt": dt, "value": batch_pairs * world * steps / dt, "routing": routing, "spread": spread,
+        res = {"dt": dt, "value": batch_pairs * world * steps / dt, "routing": routing, "spread": spread, "dumped": dumped,
                "loss": {k: float(v.detach()) for k, v in ld.items()},
                "roofline": roofline(timer, timer.steps, height, width, batch_pairs) if (timer is not None and rank == 0) else None}
         del batches, step
@@ -460,22 +534,24 @@ def main():
             raise SystemExit("--harness reference is the reference's single-process loop (the reference has no data parallelism)")
         make_step = reference_step_factory(model)
 
-    head = run(make_step, a.batch, a.height, a.width, a.steps, a.warmup, not a.no_kernel_timer)
+    head = run(make_step, a.batch, a.height, a.width, a.steps, a.warmup, a.full and not a.no_kernel_timer, count_launches=a.full,
+               dump_dir=a.dump_outputs)
     # rank 0's bucket schedule of the last step: (bucket, where it was started, ms since zero_grad)
     launch_rep = arena.launch_report() if (arena is not None and dist_on) else None
     launch_log = launch_rep["bucket_launches"] if launch_rep is not None else None
     second = None
-    if not a.no_secondary and (a.height, a.width) == (384, 448):
+    if a.full and not a.no_secondary and (a.height, a.width) == (384, 448):
         second = run(make_step, SECONDARY[0], SECONDARY[1], SECONDARY[2], SECONDARY_STEPS, 2, not a.no_kernel_timer)
 
     extra = {}
-    if world == 1 and not a.no_extra_legs and not a.no_kernel_timer:
+    extra_legs = a.full and world == 1 and not a.no_extra_legs
+    if extra_legs and not a.no_kernel_timer:
         # what the per-launch HIP events of the timed region cost (~1 000 event pairs per step): 5 more steps without them
         nt = run(make_step, a.batch, a.height, a.width, 5, 0, False)
         extra["without_kernel_timer"] = {"value": round(nt["value"], 3), "ms_per_step": round(nt["dt"] / 5 * 1e3, 3), "steps": 5,
                                          "note": "same process, same step, KernelTimer off (the headline's timed region records two "
                                                  "HIP events around every conv launch for the roofline object)"}
-    if world == 1 and not a.no_extra_legs and a.harness == "own":
+    if extra_legs and a.harness == "own":
         # what the reference's legacy `requires_grad_(True)` on the INPUT IMAGES costs (runtime.py:158-162; TrainStep(input_grads=)): 5 steps
         # of the same workload whose backward does not produce the two image gradients nobody reads.  Information, not the headline.
         def make_noig(batch_pairs, _m=make_step):
@@ -488,7 +564,7 @@ def main():
                                         "note": "TrainStep(input_grads=False): the input images are not marked requires_grad (the reference marks "
                                                 "them, runtime.py:158-162, and so does the headline); same losses, same parameter gradients, no "
                                                 "d loss / d image"}
-    if world == 1 and not a.no_extra_legs and a.harness == "own" and C.MATH == "h2":
+    if extra_legs and a.harness == "own" and C.MATH == "h2":
         # the range-free fall-back arithmetic beside the headline: 5 steps of the same workload, same process, with every
         # split-operand conv on the bf16x3 form (three bf16 pieces, six products: 24 significant bits whatever the operand range)
         C.set_math("x3")
@@ -511,7 +587,7 @@ def main():
                                   "steps": 3, "warmup": 1, "loss": f32r["loss"],
                                   "note": "IRR_CONV_MATH=f32 / conv.set_math('f32'): v_mfma_f32_32x32x2_f32 everywhere (fp32 operands, "
                                           "1/16 of the 16-bit matrix rate); same model, same batches"}
-    if world == 1 and not a.no_extra_legs and a.harness == "own" and not a.no_async_wgrad and not a.no_kernel_timer:
+    if extra_legs and a.harness == "own" and not a.no_async_wgrad and not a.no_kernel_timer:
         # (1) kernel quality without lane time-sharing: 3 steps with the weight gradients on the main stream, same process
         arena.disable_async_wgrad()
         arena.enable_direct_wgrad()
@@ -613,6 +689,12 @@ def main():
                "roofline": head["roofline"]}
         if out["roofline"] is not None:
             out["roofline"].pop("by_kernel_all", None)
+        if head["routing"] is None:
+            del out["launches_per_step"]                # counted on a step of its own: --full
+        if head["dumped"] is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "elements": head["dumped"],
+                                     "note": "last timed step: losses and outputs; float32, arrays over "
+                                             f"their share of {DUMP_BUDGET_BYTES >> 20} MiB as a seeded sample of their elements"}
         if head["spread"] is not None:
             out["ranks"] = head["spread"]
             out["ranks"]["bucket_launches_last_step"] = launch_log      # rank 0: (bucket, "backward" | "sync", ms since zero_grad)
@@ -633,7 +715,7 @@ def main():
                                 "launches_per_step": second["routing"], "roofline": second["roofline"]}
         fwd = extra.pop("_fwd", None)
         out.update(extra)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.height, a.width, quick=a.quick_cpu_baseline)
             if fwd is not None:
                 # configs[1]'s "EPE check": the oracle's eval forward on the first two pairs of the forward-only batch, timed as

@@ -16,6 +16,7 @@ Usage:  python oracle/gen_golden.py  [--out tests/golden]
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 import types
@@ -245,6 +246,10 @@ def gen_e2e(out_dir, B=2, H=128, W=192):
         d[f"{mode}_train_losses_sintel"] = np.array([float(l2["flow_loss"]), float(l2["occ_loss"]), float(l2["total_loss"])])
     set_mode(False, False)
     np.savez_compressed(os.path.join(out_dir, f"e2e_B{B}_{H}x{W}.npz"), **d)
+    # the two weight checksums summed exactly (math.fsum): independent of the reduction order of the host's torch build
+    np.savez_compressed(os.path.join(out_dir, "weight_checksum_seed0.npz"),
+                        weight_checksum_exact=np.array([math.fsum(v for t in P.values() for v in t.double().flatten().tolist()),
+                                                        math.fsum(v for t in P.values() for v in t.double().abs().flatten().tolist())]))
 
 
 def gen_e2e_big(out_dir, B=1, H=384, W=448):
@@ -438,6 +443,9 @@ def gen_init(out_dir):
                         shapes=np.array([str(tuple(sd[n].shape)) for n in names]),
                         sums=np.array([float(sd[n].double().sum()) for n in names]),
                         abssums=np.array([float(sd[n].double().abs().sum()) for n in names]),
+                        # the same fingerprints summed exactly (math.fsum): independent of the reduction order of the host's torch build
+                        fsums=np.array([math.fsum(sd[n].double().flatten().tolist()) for n in names]),
+                        fabssums=np.array([math.fsum(sd[n].double().abs().flatten().tolist()) for n in names]),
                         n_params=np.array([sum(v.numel() for v in sd.values())]))
 
 
